@@ -9,7 +9,19 @@ holds its own 1M-read shard (weak scaling; reads shard with no data-path collect
 
 One JSON line on rank 0.  `roofline` is the dominant kernel's ALGORITHMIC bytes per launch / its mean launch
 duration (HIP events on the launch stream, measured live by the library) against the 8 TB/s HBM peak.
-`cpu_baseline` is the CPU oracle (a port: the reference cannot be built here) timed on a bounded sample.
+
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line.  Everything measured or
+checked beside the headline figure runs only with --full: the per-kernel times of every kernel, the reduce alone and the
+weak figure beside a strong one (N > 1), get_posterior, the per-read kernel, the rocprofv3 --pmc passes behind
+roofline.traffic / alu, the front-end and ingest rates, `cpu_baseline` (the CPU oracle, a port: the reference cannot be
+built here, timed on a bounded sample) with its parity diff, and `end_to_end`.  What a plain run does not measure is null or absent.
+
+--dump-outputs DIR: after the timed steps, what the timed path computed in its last step, as DIR/<name>.npy (float64; a fixed,
+seeded sample of the per-read rows where the whole would pass 64 MB).  The inputs depend only on the arguments, so two builds
+run with the same arguments can be compared output for output.
+  haplocart: final_vec[P], the per-path log-likelihood sums (on rank 0: the sum over ranks)
+  euka     : the per-read results (clade, in_lik, out_lik, like, not_like, pass) and the per-clade accumulators
+  soibean  : loglike[1], the log-likelihood the last iteration's refresh returned
 """
 import argparse
 import json
@@ -58,7 +70,34 @@ def parse():
     ap.add_argument("--e2e-reads", type=int, default=10_000_000, help="reads of the file the end_to_end record runs `vgan haplocart` on (0: skip; --no-frontend skips it too)")
     ap.add_argument("--path", choices=["haplocart", "euka", "soibean"], default="haplocart",
                     help="haplocart = the BASELINE metric; euka / soibean = configs 4 / 5 as extra lines")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (the --no-* and --cpu-seconds options act on these legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64, at most 64 MB)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 60 * 10**6  # the arrays' data: with the .npy headers the files stay under 64 MB
+DUMP_SAMPLE_SEED = 0x64756D70  # the rows kept when the per-read arrays would pass the limit: the same for every run of the same size
+
+
+def dump_outputs(d, arrays, per_read=()):
+    """arrays {name: array} -> d/<name>.npy as float64.  The arrays named in per_read share their first dimension (one row a
+    read); if the whole would pass DUMP_LIMIT_BYTES they are cut to the same fixed, seeded sample of rows, in read order."""
+    import numpy as np
+    out = {k: np.ascontiguousarray(np.asarray(v), dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if per_read and total > DUMP_LIMIT_BYTES:
+        n = out[per_read[0]].shape[0]
+        fixed = total - sum(out[k].nbytes for k in per_read)
+        row = sum(out[k].nbytes // max(n, 1) for k in per_read)
+        keep = max(0, (DUMP_LIMIT_BYTES - fixed) // max(row, 1))
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=min(n, keep), replace=False))
+        for k in per_read:
+            out[k] = out[k][rows]
+    os.makedirs(d, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def pick_device(args):
@@ -217,11 +256,17 @@ def bench_euka(args):
             t = t.to(torch.float64) if t.dtype not in (torch.float64, torch.int32, torch.int64) else t
             dist.reduce(t, dst=0, op=dist.ReduceOp.SUM)
             fin[k] = t.cpu().numpy()
+    if rank == 0 and args.dump_outputs:
+        per_read = ("clade", "in_lik", "out_lik", "like", "not_like", "pass")
+        arrays = {k: dbt.out[k].cpu().numpy() for k in per_read}
+        arrays.update({k: fin[k] for k in ("clade_count", "baseshift", "bin_cov")})
+        dump_outputs(args.dump_outputs, arrays, per_read)
     if rank == 0:
-        euka_traffic = collect_traffic(args, "euka_read_kernel") if world == 1 and not args.no_pmc else None
+        pmc = args.full and world == 1 and not args.no_pmc
+        euka_traffic = collect_traffic(args, "euka_read_kernel") if pmc else None
         kb = hb.algorithmic_bytes()
         avg = ms / max(n, 1)
-        euka_issue = collect_issue(args, "euka_read_kernel", avg) if world == 1 and not args.no_pmc else None
+        euka_issue = collect_issue(args, "euka_read_kernel", avg) if pmc else None
         gbs = kb / (avg * 1e-3) / 1e9 if avg > 0 else 0.0
         out = {
             "metric": "reads/sec through euka per-read two-model likelihood (readGAM3), 75bp aDNA", "value": n_total * args.steps / elapsed,
@@ -237,7 +282,7 @@ def bench_euka(args):
                          "launches": n,
                          # this kernel is fp64-VALU bound -- the ALU-side fraction (vector instruction issue) beside the HBM one
                          "alu": euka_issue, "limiter": dict(euka_issue or {}, kind="valu (fp64) issue")}}
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"], out["parity"] = cpu_baseline_euka(g, db, alns, dm_texts, ctx, ek, args.cpu_seconds)
         print(json.dumps(out), flush=True)
 
@@ -345,13 +390,15 @@ def bench_soibean(args):
     proposals = [state() for _ in range(args.warmup + args.steps)]
     uniforms = np.log(rng.random(args.warmup + args.steps))
     it_no = 0
+    last_ll = None  # (what the last iteration's refresh returned: --dump-outputs)
 
     def iteration():
-        nonlocal cur, accepted, it_no
+        nonlocal cur, accepted, it_no, last_ll
         st, logu = proposals[it_no], uniforms[it_no]
         it_no += 1
         if fused:
             ll, _ = ctx.refresh(st[0], 0.01, freqs)
+            last_ll = ll
             if cur is None or logu < ll - cur:
                 cur = ll
                 accepted += 1
@@ -367,6 +414,7 @@ def bench_soibean(args):
         import struct
         parts = vd.all_gather_words([hi, lo, struct.unpack("<q", struct.pack("<d", nf))[0]], dev)
         ll = sb.sum_value([(h - (1 << 64) if h >= (1 << 63) else h, l, struct.unpack("<d", struct.pack("<Q", f))[0]) for h, l, f in parts])
+        last_ll = ll
         if cur is None or logu < ll - cur:
             cur = ll
             accepted += 1
@@ -381,11 +429,14 @@ def bench_soibean(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     km = ctx.kernel_ms()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loglike": [last_ll]})
     if rank == 0:
         R = hb.n_reads
-        sb_traffic = collect_traffic(args, "sb_refresh_fused_kernel" if fused else "sb_loglike_kernel") if world == 1 and not args.no_pmc else None
+        pmc = args.full and world == 1 and not args.no_pmc
+        sb_traffic = collect_traffic(args, "sb_refresh_fused_kernel" if fused else "sb_loglike_kernel") if pmc else None
         avg = km["refresh"][0] / max(km["refresh"][1], 1)
-        sb_issue = collect_issue(args, "sb_refresh_fused_kernel" if fused else "sb_loglike_kernel", avg) if world == 1 and not args.no_pmc else None
+        sb_issue = collect_issue(args, "sb_refresh_fused_kernel" if fused else "sb_loglike_kernel", avg) if pmc else None
         kb = R * 3 * 2 * (8 + 25 * 2) + R  # 2k path rows of pm (8 B) + cnt (25 x 2 B) + ok flags
         gbs = kb / (avg * 1e-3) / 1e9 if avg > 0 else 0.0
         out = {
@@ -401,7 +452,7 @@ def bench_soibean(args):
                          "traffic": sb_traffic.get("bytes") if sb_traffic else None, "traffic_detail": sb_traffic,
                          "kernel": "sb_refresh_fused_kernel" if fused else "sb_loglike_kernel + sb_finish_kernel", "algorithmic_bytes_per_launch": kb, "avg_launch_ms": avg,
                          "launches": km["refresh"][1], "alu": sb_issue}}
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"], out["parity"] = cpu_baseline_soibean(g, alns, dm, sb, state, freqs, args.cpu_seconds)
         print(json.dumps(out), flush=True)
 
@@ -812,8 +863,8 @@ def main():
         step()
     fence()
     # HIP events in the timed region around the segment kernel alone (the roofline's kernel: its average launch duration is measured
-    # live, over these very steps); the other kernels' times come from a few more steps behind the clock -- a pair of events is ~8 us of
-    # the stream's time, and three pairs a step were 4 % of it
+    # live, over these very steps); with --full the other kernels' times come from a few more steps behind the clock -- a pair of
+    # events is ~8 us of the stream's time, and three pairs a step were 4 % of it
     ctx.profile_enable(True, segment_only=(mode == hc.MODE_NODE_WEIGHTS))  # (the per-read modes' dominant kernel is the mask sweep: every kernel timed)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -821,24 +872,27 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     prof = ctx.profile_read()
-    ctx.profile_enable(True)
-    n_extra = max(1, min(args.steps, 10))
-    for _ in range(n_extra):
-        step()
-    fence()
-    prof_all = ctx.profile_read()
-    for k, v in prof_all.items():
-        if k != "segment" and mode == hc.MODE_NODE_WEIGHTS:
-            prof[k] = (v[0] * args.steps / n_extra, v[1] * args.steps // n_extra)  # (scaled to the timed steps: per-step figures below)
+    final_host = final_dev.cpu().numpy().copy()           # the last timed step's result, complete on rank 0
+    if args.full:
+        ctx.profile_enable(True)
+        n_extra = max(1, min(args.steps, 10))
+        for _ in range(n_extra):
+            step()
+        fence()
+        prof_all = ctx.profile_read()
+        for k, v in prof_all.items():
+            if k != "segment" and mode == hc.MODE_NODE_WEIGHTS:
+                prof[k] = (v[0] * args.steps / n_extra, v[1] * args.steps // n_extra)  # (scaled to the timed steps: per-step figures below)
     ctx.profile_enable(False)
     elapsed = vd.all_reduce_max(elapsed, dev)            # MAX over ranks
     total_reads = vd.all_reduce_sum(float(n_reads), dev)  # whole-job reads per step
-    final_host = final_dev.cpu().numpy().copy()           # complete on rank 0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"final_vec": final_host})
 
     # ---- per-rank kernel times and the cost of the reduce alone (outside the timed region)
     my_kernels = {k: v[0] / max(args.steps, 1) for k, v in prof.items()}
-    per_rank, reduce_ms = [my_kernels], None
-    if world > 1:
+    per_rank, reduce_ms = None, None
+    if args.full and world > 1:
         gathered = [None] * world
         dist.all_gather_object(gathered, {"rank": rank, "reads": n_reads, "kernel_ms_per_step": my_kernels})
         per_rank = gathered
@@ -852,7 +906,7 @@ def main():
     # ---- N > 1: who took part (is RCCL really running over N ranks on N devices?), and, beside the strong figure, the weak one
     # (the first 1M-read device batch of every rank: configs[1] per GPU)
     dist_info, weak_beside = None, None
-    if world > 1:
+    if args.full and world > 1:
         props = torch.cuda.get_device_properties(dev)
         mine = {"rank": rank, "local_rank": local_rank, "device_index": torch.cuda.current_device(), "device_name": props.name,
                 "pci_bus_id": getattr(props, "pci_bus_id", None), "uuid": str(getattr(props, "uuid", "")) or None}
@@ -886,7 +940,7 @@ def main():
 
     # ---- a9 (get_posterior.cpp:87-127) on rank 0, timed on its own: host tree walk + upload + one kernel
     posterior_ms, posterior_top = None, None
-    if rank == 0:
+    if args.full and rank == 0:
         pred = graph.path_names[ctx.argmax(final_host)]
         ctx.posterior(final_host, pred)
         t0 = time.perf_counter()
@@ -898,7 +952,7 @@ def main():
     # ---- the reference's loop order (one mask row per segment) measured beside the default mode: the kernel
     # BASELINE.json's north_star puts the >= 30 % HBM-roofline target on.  Outside the timed region.
     per_read = None
-    if rank == 0 and mode == hc.MODE_NODE_WEIGHTS and not args.no_extra:
+    if args.full and rank == 0 and mode == hc.MODE_NODE_WEIGHTS and not args.no_extra:
         per_read = {}
         db0 = batches[0]
         row_bytes = 8 * ((graph.n_paths + 63) // 64) + 4 + 8
@@ -932,7 +986,7 @@ def main():
         avg_ms = k_ms / max(k_n, 1)
         kernel_name = {"segment": "hc_segment", "sweep_segments": "hc_sweep_kernel"}[kname]
         traffic, issue = None, None
-        if world == 1 and not args.no_pmc and args.scaling == "weak":
+        if args.full and world == 1 and not args.no_pmc and args.scaling == "weak":
             ksub = kernel_name if kname == "segment" else "hc_sweep_kernel<10, false>"
             traffic = collect_traffic(args, ksub)
             issue = collect_issue(args, ksub, avg_ms)
@@ -990,14 +1044,14 @@ def main():
             "parity": None,
             "per_read_kernel": per_read,
         }
-        if world == 1 and not args.no_frontend:
+        if args.full and world == 1 and not args.no_frontend:
             out["front_end"] = front_end_rates(graph, hc, args.seed, ctx=ctx)
-        if world == 1 and not args.no_ingest and mode == hc.MODE_NODE_WEIGHTS:
+        if args.full and world == 1 and not args.no_ingest and mode == hc.MODE_NODE_WEIGHTS:
             batches.clear()  # (the resident batch's HBM is not needed any more)
             out["ingest"] = ingest_rates(graph, hc, ctx, dev, args)
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"], out["parity"] = cpu_baseline(graph, alns0, args.cpu_seconds, ctx, hc)
-        if world == 1 and not args.no_frontend and args.e2e_reads > 0 and mode == hc.MODE_NODE_WEIGHTS and args.path == "haplocart":
+        if args.full and world == 1 and not args.no_frontend and args.e2e_reads > 0 and mode == hc.MODE_NODE_WEIGHTS and args.path == "haplocart":
             try:
                 del ctx  # (the binary brings its own contexts up: this process's device memory goes first)
                 out["end_to_end"] = end_to_end(graph, hc, args)

@@ -66,7 +66,7 @@ def test_two_ranks_on_one_gpu_reduce_product_vectors(tmp_path):
 
 
 def _bench(*extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-extra",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-extra",
            "--no-pmc", "--no-frontend", "--no-ingest"] + list(extra)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
@@ -180,7 +180,7 @@ def _n_gpus():
     return N.lib().vgan_device_count()
 
 
-@pytest.mark.skipif("_n_gpus() < 2")
+@pytest.mark.skipif("_n_gpus() < 2", reason="needs 2 GPUs")
 def test_rccl_reduce_between_two_distinct_gpus(tmp_path, monkeypatch):
     """Needs two GPUs (skipped on the one-GPU rig): the RCCL branch of vgan_hc_reduce -- one communicator per device set,
     created on the first reduce and reused by the second -- and the CLI with --gpus 0,1, against the one-context result."""

@@ -3,6 +3,7 @@
 # usage: tools/gpu_profile.sh <tag> <bench args...>
 set -x
 tag=$1; shift
+set -- "$@" --full  # the whole run under the profiler: the per-kernel steps, get_posterior and the per-read kernel included
 export TMPDIR=/tmp
 mkdir -p gpurun_out/prof_$tag
 cd /tmp
