@@ -127,6 +127,23 @@ def test_soibean_cli_validation_errors(tmp_path):
         assert r.returncode == 1 and "no HIP device" in r.stderr and not list(tmp_path.glob("o_*"))
 
 
+@pytest.mark.parametrize("tool", ["haplocart", "euka", "soibean"])
+def test_gpu_list_errors_name_their_source(tool, tmp_path):
+    """--gpus and VGAN_GPUS go through one parser: a bad entry is an error that names where it came from."""
+    for f in ("euka_db.gfa", "euka_db.clade", "euka_db.bins", "T.gfa"):
+        (tmp_path / f).touch()
+    (tmp_path / "tree_dir").mkdir()
+    (tmp_path / "tree_dir" / "T.new.dnd").touch()
+    args = {"haplocart": ["-g", "/dev/null"], "euka": ["--euka_dir", str(tmp_path), "-g", "/dev/null"],
+            "soibean": ["--dbprefix", "T", "--soibean_dir", str(tmp_path), "-g", "/dev/null"]}[tool]
+    env = {k: v for k, v in os.environ.items() if k != "VGAN_GPUS"}
+    for bad, word in (("x", "needs an integer"), ("0,-1", "non-negative"), ("0,,1", "needs an integer")):
+        r = subprocess.run([VGAN, tool] + args + ["--gpus", bad], capture_output=True, text=True, env=env)
+        assert r.returncode == 1 and "--gpus" in r.stderr and word in r.stderr, (bad, r.stderr)
+        r = subprocess.run([VGAN, tool] + args, capture_output=True, text=True, env=dict(env, VGAN_GPUS=bad))
+        assert r.returncode == 1 and "VGAN_GPUS" in r.stderr and word in r.stderr, (bad, r.stderr)
+
+
 def test_cli_needs_a_gpu_not_a_fallback(tmp_path):
     if N.lib().vgan_device_count() > 0:
         pytest.skip("a GPU is visible")

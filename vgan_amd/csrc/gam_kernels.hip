@@ -1011,7 +1011,6 @@ int exclusive_sum(vgan_gamdev *g, const uint32_t *in, uint32_t *out, size_t n) {
     if (hipcub::DeviceScan::ExclusiveSum(g->cub_tmp.p, tmp, in, out, (int)n, g->stream) != hipSuccess) return fail(VGAN_ENODEV, "vgan_gamdev_parse: scan failed");
     return VGAN_OK;
 }
-double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 } // namespace
 
 namespace {

@@ -6,7 +6,13 @@
 
 #include <algorithm>
 #include <chrono>
+#include <condition_variable>
 #include <cstdlib>
+#include <deque>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
 #include <vector>
 
 #include "gam_device.h"
@@ -203,6 +209,132 @@ int gampipe_run(const void *bytes, uint64_t n, const std::vector<int> &lane_devi
                 vgan_gampipe_stats *stats);
 // the options a run takes when the caller leaves them open (piece size from the input's size, slots, tail room; VGAN_GAMPIPE_* environment)
 vgan_gampipe_opts gampipe_defaults(const vgan_gampipe_opts *o, uint64_t n_bytes, int n_lanes);
+
+inline double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
+// ---- a subcommand's run over the pipeline (vgan_<tool>_gam_start / attach / finish): the pipeline starts on a coordinator thread before
+// the subcommand has its contexts; its pieces wait in consume() until attach brings them.  The reads the device flatten of a piece leaves
+// go through the host on jobs of their own, joined at the finish.
+struct GamJob {
+    std::thread t;
+    int rc = VGAN_OK;
+    std::string err;
+};
+template <class Ctx, class Flat, class Job = GamJob> struct GamRun : GamConsumer {
+    const char *tool = ""; // (the C-ABI's name: vgan_<tool>_gam_*)
+    std::vector<int> devices;
+    const void *bytes = nullptr;
+    uint64_t n = 0;
+    vgan_gampipe_opts opts{};
+    std::thread coord;
+    int rc = VGAN_OK;
+    std::string err;
+    vgan_gampipe_stats pst{};
+    // what attach brings
+    std::mutex mu;
+    std::condition_variable cv;
+    bool attached = false, gave_up = false;
+    std::vector<Ctx *> ctx;
+    const vgan_graph *graph = nullptr;
+    std::vector<Flat *> df;         // per lane, made by its first piece
+    std::deque<std::mutex> lane_mu; // (the lane's context, its stream and its flatten object: one piece at a time)
+    std::vector<std::shared_ptr<Job>> bg;
+    uint64_t n_host_reads = 0, n_device_reads = 0;
+    double ms_wait_contexts = 0;
+    int host_threads = 2;
+
+    void aborted() override {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            gave_up = true;
+        }
+        cv.notify_all();
+    }
+    // consume()'s prologue: waits for the contexts; the piece's read count (< 2^32 reads in the file), or an error
+    int64_t piece_reads(vgan_gamdev *g, uint64_t read_base) {
+        {
+            const auto t0 = std::chrono::steady_clock::now();
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return attached || gave_up; });
+            if (!attached) return fail(VGAN_ESTATE, "vgan_%s_gam: no contexts were attached", tool);
+            ms_wait_contexts = std::max(ms_wait_contexts, ms_since(t0));
+        }
+        uint64_t sz[8];
+        (void)vgan_gamdev_sizes(g, sz, nullptr);
+        if (read_base + sz[2] > 0xFFFFFFF0ull) return fail(VGAN_ERANGE, "vgan_%s_gam: more than 2^32 reads", tool);
+        return (int64_t)sz[2];
+    }
+    // the finish's start: nobody brings contexts any more (the pieces that wait for them give up), the pipeline and the host's jobs are
+    // joined, the first error kept
+    void join() {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            if (!attached) gave_up = true;
+        }
+        cv.notify_all();
+        if (coord.joinable()) coord.join();
+        for (auto &j : bg) {
+            if (j->t.joinable()) j->t.join();
+            if (j->rc < 0 && rc >= 0) {
+                rc = j->rc;
+                err = "the reads left to the host: " + j->err;
+            }
+        }
+        pst.n_host_reads = n_host_reads;
+        pst.n_device_reads = n_device_reads;
+        pst.ms_wait_contexts = ms_wait_contexts;
+    }
+};
+
+// vgan_<tool>_gam_start: the pipeline on its coordinator thread.  set_up: the subcommand's own options and members, before it starts.
+template <class Run, class SetUp>
+int gamrun_start(const char *tool, const int *devices, int n_lanes, const void *bytes, uint64_t n, const vgan_gampipe_opts *opts, Run **out, SetUp set_up) {
+    if (!devices || n_lanes <= 0 || (!bytes && n) || !out) return fail(VGAN_EINVAL, "vgan_%s_gam_start: null argument", tool);
+    auto *r = new Run();
+    r->tool = tool;
+    r->devices.assign(devices, devices + n_lanes);
+    r->bytes = bytes;
+    r->n = n;
+    r->opts = gampipe_defaults(opts, n, n_lanes);
+    r->df.assign((size_t)n_lanes, nullptr);
+    r->lane_mu.resize((size_t)n_lanes);
+    set_up(*r);
+    const int cpus = r->opts.n_threads > 0 ? r->opts.n_threads : (int)usable_cpus();
+    r->host_threads = std::max(1, std::min(8, cpus / std::max(1, n_lanes * r->opts.slots)));
+    r->coord = std::thread([r] {
+        r->rc = gampipe_run(r->bytes, r->n, r->devices, r->opts, *r, &r->pst);
+        if (r->rc < 0) r->err = last_error();
+    });
+    *out = r;
+    return VGAN_OK;
+}
+
+// vgan_<tool>_gam_attach: the contexts (one per lane) and the graph the waiting pieces need
+template <class Ctx, class Flat, class Job>
+int gamrun_attach(const char *tool, GamRun<Ctx, Flat, Job> *r, Ctx *const *ctxs, int n_ctx, const vgan_graph *graph) {
+    if (!r || !ctxs || !graph) return fail(VGAN_EINVAL, "vgan_%s_gam_attach: null argument", tool);
+    if (n_ctx != (int)r->devices.size()) return fail(VGAN_EINVAL, "vgan_%s_gam_attach: %d contexts for %zu lanes", tool, n_ctx, r->devices.size());
+    {
+        std::lock_guard<std::mutex> lk(r->mu);
+        if (r->attached) return fail(VGAN_ESTATE, "vgan_%s_gam_attach: called twice", tool);
+        r->ctx.assign(ctxs, ctxs + n_ctx);
+        r->graph = graph;
+        r->attached = true;
+    }
+    r->cv.notify_all();
+    return VGAN_OK;
+}
+
+// The reads of a piece the device flatten leaves to the host (euka, soibean): their messages come down on the slot thread -- the piece's
+// object is the next piece's once consume() returns -- and are parsed behind its back.
+struct LeftReads {
+    std::vector<uint32_t> where; // the reads' places among the file's mapped reads (empty: the device took every read)
+    std::vector<uint64_t> offs;
+    std::vector<uint8_t> msgs;
+    int pick(vgan_gamdev *g, const uint8_t *mask, uint64_t R, uint64_t read_base, const char *tool);
+    // one alnset of as many reads as messages (the messages are let go)
+    int parse(int n_threads, const char *tool, vgan_alnset &merged);
+};
 } // namespace gd
 } // namespace vgan
 struct vgan_hc_devflat;

@@ -35,24 +35,6 @@ using namespace vgan::gd;
 
 namespace {
 
-double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-
-// piece_bytes = 0: a piece is a twenty-fourth of a lane's share of the file, within 32..192 MB -- a short file still gives every slot
-// several pieces to overlap (a 1.5 GB file in pieces of 192 MB was three rounds of three slots: 1.1 s against 0.9 in pieces of 64 MB),
-// a long one is not cut finer than the per-piece costs (a dozen stream synchronisations, the framing's hand-over) are worth
-vgan_gampipe_opts with_defaults(const vgan_gampipe_opts *o, uint64_t n_bytes = 0, int n_lanes = 1) {
-    vgan_gampipe_opts r{};
-    if (o) r = *o;
-    if (const char *e = getenv("VGAN_GAMPIPE_PIECE")) r.piece_bytes = strtoull(e, nullptr, 10);
-    if (const char *e = getenv("VGAN_GAMPIPE_SLOTS")) r.slots = atoi(e);
-    if (r.slots <= 0) r.slots = 3;
-    if (r.piece_bytes == 0)
-        r.piece_bytes = n_bytes ? std::min<uint64_t>(192ull << 20, std::max<uint64_t>(32ull << 20, n_bytes / (uint64_t)(8 * r.slots * std::max(1, n_lanes)))) : 192ull << 20;
-    if (r.slots > 16) r.slots = 16;
-    if (r.tail_bytes == 0) r.tail_bytes = 8ull << 20;
-    return r;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- the pieces
 struct PiecePlan {
     uint64_t in0 = 0, in1 = 0;       // the piece's bytes in the file: its first member's header .. its last member's trailer
@@ -338,14 +320,28 @@ struct Pipe {
 
 } // namespace
 
-vgan_gampipe_opts vgan::gd::gampipe_defaults(const vgan_gampipe_opts *o, uint64_t n_bytes, int n_lanes) { return with_defaults(o, n_bytes, n_lanes); }
+// piece_bytes = 0: a piece is a twenty-fourth of a lane's share of the file, within 32..192 MB -- a short file still gives every slot
+// several pieces to overlap (a 1.5 GB file in pieces of 192 MB was three rounds of three slots: 1.1 s against 0.9 in pieces of 64 MB),
+// a long one is not cut finer than the per-piece costs (a dozen stream synchronisations, the framing's hand-over) are worth
+vgan_gampipe_opts vgan::gd::gampipe_defaults(const vgan_gampipe_opts *o, uint64_t n_bytes, int n_lanes) {
+    vgan_gampipe_opts r{};
+    if (o) r = *o;
+    if (const char *e = getenv("VGAN_GAMPIPE_PIECE")) r.piece_bytes = strtoull(e, nullptr, 10);
+    if (const char *e = getenv("VGAN_GAMPIPE_SLOTS")) r.slots = atoi(e);
+    if (r.slots <= 0) r.slots = 3;
+    if (r.piece_bytes == 0)
+        r.piece_bytes = n_bytes ? std::min<uint64_t>(192ull << 20, std::max<uint64_t>(32ull << 20, n_bytes / (uint64_t)(8 * r.slots * std::max(1, n_lanes)))) : 192ull << 20;
+    if (r.slots > 16) r.slots = 16;
+    if (r.tail_bytes == 0) r.tail_bytes = 8ull << 20;
+    return r;
+}
 
 int vgan::gd::gampipe_run(const void *bytes, uint64_t n, const std::vector<int> &lane_devices, const vgan_gampipe_opts &opts_in, GamConsumer &consumer,
                           vgan_gampipe_stats *stats) {
     if (stats) memset(stats, 0, sizeof *stats);
     if ((!bytes && n) || lane_devices.empty()) return fail(VGAN_EINVAL, "gampipe_run: null argument");
     const int N = (int)lane_devices.size();
-    vgan_gampipe_opts o = with_defaults(&opts_in, n, N);
+    vgan_gampipe_opts o = gampipe_defaults(&opts_in, n, N);
     const auto t0 = std::chrono::steady_clock::now();
     // ---- what the lanes will hold of their devices' memory against what is free there: smaller pieces, fewer slots, or not at all
     // (S sets of {a piece's bytes, their inflated form, the parse's arrays ~1.1 x that} + one flattened piece ~1.3 x per lane)
@@ -410,7 +406,7 @@ int vgan::gd::gampipe_run(const void *bytes, uint64_t n, const std::vector<int> 
 extern "C" int64_t vgan_gampipe_plan(const void *bytes, uint64_t n, const vgan_gampipe_opts *opts, uint64_t *piece_in_off, uint64_t *piece_in_bytes,
                                      uint64_t *piece_out_bytes, int64_t cap) {
     if (!bytes && n) return fail(VGAN_EINVAL, "vgan_gampipe_plan: null argument");
-    const vgan_gampipe_opts o = with_defaults(opts, n, 1);
+    const vgan_gampipe_opts o = gampipe_defaults(opts, n, 1);
     Cutter c(bytes, n, o.piece_bytes, 0xE0000000ull - o.tail_bytes);
     int64_t k = 0;
     PiecePlan pc;
@@ -430,7 +426,7 @@ struct vgan_gampipe_carry {
 extern "C" void vgan_gampipe_carry_free(vgan_gampipe_carry *c) { delete c; }
 extern "C" int vgan_gampipe_parse_piece(vgan_gamdev *g, const void *bytes, uint64_t n, const vgan_gampipe_opts *opts, int64_t piece, vgan_gampipe_carry **carry) {
     if (!g || (!bytes && n) || !carry || piece < 0) return fail(VGAN_EINVAL, "vgan_gampipe_parse_piece: null argument");
-    const vgan_gampipe_opts o = with_defaults(opts, n, 1);
+    const vgan_gampipe_opts o = gampipe_defaults(opts, n, 1);
     Cutter c(bytes, n, o.piece_bytes, 0xE0000000ull - o.tail_bytes);
     PiecePlan pc, nxt;
     if (!c.get((size_t)piece, pc)) return fail(c.is_bad() ? VGAN_EIO : VGAN_EINVAL, "vgan_gampipe_parse_piece: the file has no piece %lld", (long long)piece);
@@ -445,53 +441,50 @@ extern "C" int vgan_gampipe_parse_piece(vgan_gamdev *g, const void *bytes, uint6
     return VGAN_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------ the reads left to the host
+int vgan::gd::LeftReads::pick(vgan_gamdev *g, const uint8_t *mask, uint64_t R, uint64_t read_base, const char *tool) {
+    for (uint64_t i = 0; i < R; ++i)
+        if (mask[(size_t)i]) where.push_back((uint32_t)(read_base + i));
+    if (where.empty()) return VGAN_OK;
+    uint64_t nm = 0, nb = 0;
+    int r;
+    if ((r = vgan_gamdev_pick(g, mask, &nm, &nb)) < 0) return r;
+    if (nm != where.size()) return fail(VGAN_ESTATE, "vgan_%s_gam: %llu messages picked for %zu reads", tool, (unsigned long long)nm, where.size());
+    offs.resize((size_t)nm + 1);
+    msgs.resize((size_t)std::max<uint64_t>(nb, 1));
+    return vgan_gamdev_picked(g, offs.data(), msgs.data());
+}
+
+int vgan::gd::LeftReads::parse(int n_threads, const char *tool, vgan_alnset &merged) {
+    vgan_alnparts *parts = nullptr;
+    // (keep_unmapped: the parse on the device dropped identity == 0 already; every message handed back is a read)
+    int r = vgan_alnparts_from_messages(msgs.data(), offs.data(), (int64_t)where.size(), 1, n_threads, &parts);
+    std::vector<uint64_t>().swap(offs);
+    std::vector<uint8_t>().swap(msgs);
+    if (r < 0) return r;
+    merge_alnsets(parts->parts, merged);
+    vgan_alnparts_free(parts);
+    if (merged.n_reads() != (int64_t)where.size())
+        return fail(VGAN_ESTATE, "vgan_%s_gam: %lld reads parsed of %zu messages", tool, (long long)merged.n_reads(), where.size());
+    return VGAN_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------------ HaploCart
 // vgan haplocart's consumer: device flatten of the piece into the packed batch + the segment kernel, on the lane's context; the reads the
 // device flatten leaves (indels, soft clips, long reads) come back as their messages and go through the host's parser and flatten,
 // beside the device's write pass.
 namespace {
-struct LeftJob { // the reads of one piece that the device flatten leaves to the host
-    std::thread t;
+struct LeftJob : GamJob { // the reads of one piece that the device flatten leaves to the host
     std::vector<uint8_t> mask;
     uint64_t n = 0;
-    int rc = VGAN_OK;
-    std::string err;
     std::mutex m;
     std::condition_variable cv;
     bool dev_done = false; // the messages are down: the piece's device object is free
 };
 } // namespace
-struct vgan_hc_gamrun : GamConsumer {
-    std::vector<std::shared_ptr<LeftJob>> bg;
-    std::vector<int> devices;
-    const void *bytes = nullptr;
-    uint64_t n = 0;
-    vgan_gampipe_opts opts{};
-    std::thread coord;
-    int rc = VGAN_OK;
-    std::string err;
-    vgan_gampipe_stats pst{};
-    // what attach brings
-    std::mutex mu;
-    std::condition_variable cv;
-    bool attached = false, gave_up = false;
-    std::vector<vgan_hc_ctx *> ctx;
-    const vgan_graph *graph = nullptr;
-    std::vector<vgan_hc_devflat *> df;
-    std::deque<std::mutex> lane_mu;
+struct vgan_hc_gamrun : GamRun<vgan_hc_ctx, vgan_hc_devflat, LeftJob> {
     vgan_hc_flatten_stats fst{};
-    uint64_t n_host_reads = 0, n_device_reads = 0;
-    size_t df_bytes = 0;
-    double ms_wait_contexts = 0;
-    int host_threads = 2;
 
-    void aborted() override {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            gave_up = true;
-        }
-        cv.notify_all();
-    }
     int hand_over(vgan_hc_ctx *cx, vgan_hc_host_batch *hb) {
         vgan_hc_batch b;        // the reads outside the tile contract (long reads, ...): the general kernel
         vgan_hc_packed_view pk; // everything else, in the segment kernel's own layout as the flatten step wrote it
@@ -501,18 +494,9 @@ struct vgan_hc_gamrun : GamConsumer {
         return VGAN_OK;
     }
     int consume(int lane, vgan_gamdev *g, uint64_t read_base, const uint8_t *d_dup, int64_t) override {
-        {
-            const auto t0 = std::chrono::steady_clock::now();
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return attached || gave_up; });
-            if (!attached) return fail(VGAN_ESTATE, "vgan_hc_gam: no contexts were attached");
-            ms_wait_contexts = std::max(ms_wait_contexts, ms_since(t0));
-        }
+        const int64_t R = piece_reads(g, read_base);
+        if (R < 0) return (int)R;
         vgan_hc_ctx *cx = ctx[(size_t)lane];
-        uint64_t sz[8];
-        (void)vgan_gamdev_sizes(g, sz, nullptr);
-        const uint64_t R = sz[2];
-        if (read_base + R > 0xFFFFFFF0ull) return fail(VGAN_ERANGE, "vgan_hc_gam: more than 2^32 reads");
         // the reads the device flatten leaves: their messages come down (on a thread of its own from the moment the mask is known, beside
         // the device's offsets and write pass) -- the piece's slot waits for that much, the object's buffers are free then -- and the
         // host parses, flattens and hands them over behind the slot's back, while it already takes its next piece
@@ -580,7 +564,7 @@ struct vgan_hc_gamrun : GamConsumer {
         const auto tc0 = std::chrono::steady_clock::now();
         double t_lock = 0, t_flat = 0;
         {
-            std::lock_guard<std::mutex> lk(lane_mu[(size_t)lane]); // (the lane's context, its stream and its flatten object: one piece at a time)
+            std::lock_guard<std::mutex> lk(lane_mu[(size_t)lane]);
             t_lock = ms_since(tc0);
             if (!df[(size_t)lane] && (r = vgan_hc_devflat_create(cx, graph, &df[(size_t)lane])) < 0) return r;
             r = vgan_hc_devflat_run_gamdev_cb(df[(size_t)lane], g, d_dup, d_dup ? 1 : 0, (uint32_t)read_base, &pk, job->mask.data(), &st, &Hook::go, &hook);
@@ -610,62 +594,19 @@ struct vgan_hc_gamrun : GamConsumer {
 };
 
 extern "C" int vgan_hc_gam_start(const int *devices, int n_lanes, const void *bytes, uint64_t n, const vgan_gampipe_opts *opts, vgan_hc_gamrun **out) {
-    if (!devices || n_lanes <= 0 || (!bytes && n) || !out) return fail(VGAN_EINVAL, "vgan_hc_gam_start: null argument");
-    auto *r = new vgan_hc_gamrun();
-    r->devices.assign(devices, devices + n_lanes);
-    r->bytes = bytes;
-    r->n = n;
-    r->opts = with_defaults(opts, n, n_lanes);
-    r->df.assign((size_t)n_lanes, nullptr);
-    r->lane_mu.resize((size_t)n_lanes);
-    const int cpus = r->opts.n_threads > 0 ? r->opts.n_threads : (int)usable_cpus();
-    r->host_threads = std::max(1, std::min(8, cpus / std::max(1, n_lanes * r->opts.slots)));
-    r->coord = std::thread([r] {
-        r->rc = gampipe_run(r->bytes, r->n, r->devices, r->opts, *r, &r->pst);
-        if (r->rc < 0) r->err = last_error();
-    });
-    *out = r;
-    return VGAN_OK;
+    return gamrun_start("hc", devices, n_lanes, bytes, n, opts, out, [](vgan_hc_gamrun &) {});
 }
 
-extern "C" int vgan_hc_gam_attach(vgan_hc_gamrun *r, vgan_hc_ctx *const *ctxs, int n_ctx, const vgan_graph *graph) {
-    if (!r || !ctxs || !graph) return fail(VGAN_EINVAL, "vgan_hc_gam_attach: null argument");
-    if (n_ctx != (int)r->devices.size()) return fail(VGAN_EINVAL, "vgan_hc_gam_attach: %d contexts for %zu lanes", n_ctx, r->devices.size());
-    {
-        std::lock_guard<std::mutex> lk(r->mu);
-        if (r->attached) return fail(VGAN_ESTATE, "vgan_hc_gam_attach: called twice");
-        r->ctx.assign(ctxs, ctxs + n_ctx);
-        r->graph = graph;
-        r->attached = true;
-    }
-    r->cv.notify_all();
-    return VGAN_OK;
-}
+extern "C" int vgan_hc_gam_attach(vgan_hc_gamrun *r, vgan_hc_ctx *const *ctxs, int n_ctx, const vgan_graph *graph) { return gamrun_attach("hc", r, ctxs, n_ctx, graph); }
 
 extern "C" int vgan_hc_gam_finish(vgan_hc_gamrun *r, vgan_hc_flatten_stats *stats, vgan_gampipe_stats *pstats) {
     if (!r) return fail(VGAN_EINVAL, "vgan_hc_gam_finish: null argument");
-    {
-        std::lock_guard<std::mutex> lk(r->mu);
-        if (!r->attached) r->gave_up = true; // (nobody will bring contexts any more: the pieces that wait for them give up)
-    }
-    r->cv.notify_all();
-    if (r->coord.joinable()) r->coord.join();
-    for (auto &j : r->bg) { // the host's share of the pieces (parse, flatten, hand-over of the reads the device left)
-        if (j->t.joinable()) j->t.join();
-        if (j->rc < 0 && r->rc >= 0) {
-            r->rc = j->rc;
-            r->err = "the reads left to the host: " + j->err;
-        }
-    }
+    r->join();
     for (size_t l = 0; l < r->df.size(); ++l) {
         if (r->df[l] && l < r->ctx.size()) (void)vgan_hc_synchronize(r->ctx[l]); // (the segment kernel reads the flatten object's buffers)
-        r->df_bytes += hc_devflat_device_bytes(r->df[l]);
+        r->pst.device_bytes += hc_devflat_device_bytes(r->df[l]);
         vgan_hc_devflat_free(r->df[l]);
     }
-    r->pst.device_bytes += r->df_bytes;
-    r->pst.n_host_reads = r->n_host_reads;
-    r->pst.n_device_reads = r->n_device_reads;
-    r->pst.ms_wait_contexts = r->ms_wait_contexts;
     if (stats) *stats = r->fst;
     if (pstats) *pstats = r->pst;
     const int rc = r->rc;
@@ -722,68 +663,30 @@ struct DevArr { // a device array that grows
         cap = 0;
     }
 };
-struct EukaLeftJob {
-    std::thread t;
-    int rc = VGAN_OK;
-    std::string err;
+struct EukaLeftJob : GamJob {
+    LeftReads left;
 };
 } // namespace
 
-struct vgan_euka_gamrun : GamConsumer {
-    std::vector<int> devices;
-    const void *bytes = nullptr;
-    uint64_t n = 0;
-    vgan_gampipe_opts opts{};
-    std::thread coord;
-    int rc = VGAN_OK;
-    std::string err;
-    vgan_gampipe_stats pst{};
-    std::mutex mu;
-    std::condition_variable cv;
-    bool attached = false, gave_up = false;
-    std::vector<vgan_euka_ctx *> ctx;
-    const vgan_graph *graph = nullptr;
-    std::vector<vgan_euka_devflat *> df;
+struct vgan_euka_gamrun : GamRun<vgan_euka_ctx, vgan_euka_devflat, EukaLeftJob> {
     std::vector<DevArr> o_clade, o_d, o_pass;
-    std::deque<std::mutex> lane_mu;
-    std::vector<std::shared_ptr<EukaLeftJob>> bg;
     // per processed read, in the order the pieces came (sorted by `idx` at the end)
     std::vector<uint32_t> idx;
     std::vector<int32_t> clade;
     std::vector<uint8_t> pass;
     std::vector<uint16_t> len;
     int64_t n_bad = 0;
-    uint64_t n_host_reads = 0, n_device_reads = 0;
-    size_t df_bytes = 0;
-    double ms_wait_contexts = 0;
-    int host_threads = 2;
 
-    void aborted() override {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            gave_up = true;
-        }
-        cv.notify_all();
-    }
     int consume(int lane, vgan_gamdev *g, uint64_t read_base, const uint8_t *, int64_t) override {
-        {
-            const auto t0 = std::chrono::steady_clock::now();
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return attached || gave_up; });
-            if (!attached) return fail(VGAN_ESTATE, "vgan_euka_gam: no contexts were attached");
-            ms_wait_contexts = std::max(ms_wait_contexts, ms_since(t0));
-        }
+        const int64_t R = piece_reads(g, read_base);
+        if (R < 0) return (int)R;
         vgan_euka_ctx *cx = ctx[(size_t)lane];
-        uint64_t sz[8];
-        (void)vgan_gamdev_sizes(g, sz, nullptr);
-        const uint64_t R = sz[2];
-        if (read_base + R > 0xFFFFFFF0ull) return fail(VGAN_ERANGE, "vgan_euka_gam: more than 2^32 reads");
         std::vector<uint8_t> mask((size_t)R, 0);
         std::vector<int32_t> h_clade;
         std::vector<uint8_t> h_pass;
         int r;
         {
-            std::lock_guard<std::mutex> lk(lane_mu[(size_t)lane]); // (the lane's context, its stream and its flatten object: one piece at a time)
+            std::lock_guard<std::mutex> lk(lane_mu[(size_t)lane]);
             const size_t l = (size_t)lane;
             if (!df[l] && (r = vgan_euka_devflat_create(cx, graph, &df[l])) < 0) return r;
             vgan_euka_batch b;
@@ -812,32 +715,16 @@ struct vgan_euka_gamrun : GamConsumer {
                 n_device_reads += nr;
             }
         }
-        // ---- the reads left to the host: their messages down now (the object's buffers are the next piece's after this call), the rest behind
-        std::vector<uint32_t> where;
-        for (uint64_t i = 0; i < R; ++i)
-            if (mask[(size_t)i]) where.push_back((uint32_t)(read_base + i));
-        if (where.empty()) return VGAN_OK;
-        uint64_t nm = 0, nb = 0;
-        if ((r = vgan_gamdev_pick(g, mask.data(), &nm, &nb)) < 0) return r;
-        if (nm != where.size()) return fail(VGAN_ESTATE, "vgan_euka_gam: %llu messages picked for %zu reads", (unsigned long long)nm, where.size());
-        auto offs = std::make_shared<std::vector<uint64_t>>((size_t)nm + 1);
-        auto msgs = std::make_shared<std::vector<uint8_t>>((size_t)std::max<uint64_t>(nb, 1));
-        if ((r = vgan_gamdev_picked(g, offs->data(), msgs->data())) < 0) return r;
         auto job = std::make_shared<EukaLeftJob>();
+        if ((r = job->left.pick(g, mask.data(), (uint64_t)R, read_base, tool)) < 0 || job->left.where.empty()) return r;
         vgan_euka_gamrun *self = this;
-        auto whr = std::make_shared<std::vector<uint32_t>>(std::move(where));
-        job->t = std::thread([self, job, offs, msgs, whr, cx, lane] {
-            vgan_alnparts *parts = nullptr;
+        job->t = std::thread([self, job, cx, lane] {
             vgan_alnset merged;
             vgan_euka_host_batch *hb = nullptr;
             vgan_euka_flatten_stats st{};
-            // (keep_unmapped: the parse on the device dropped identity == 0 already; every message handed back is a read)
-            if ((job->rc = vgan_alnparts_from_messages(msgs->data(), offs->data(), (int64_t)whr->size(), 1, self->host_threads, &parts)) >= 0) {
-                merge_alnsets(parts->parts, merged);
-                vgan_alnparts_free(parts);
-                if (merged.n_reads() != (int64_t)whr->size()) job->rc = fail(VGAN_ESTATE, "vgan_euka_gam: %lld reads parsed of %zu messages", (long long)merged.n_reads(), whr->size());
-            }
-            if (job->rc >= 0) job->rc = vgan_euka_flatten(self->graph, &merged, 0, merged.n_reads(), self->host_threads, &hb, &st);
+            const std::vector<uint32_t> &where = job->left.where;
+            if ((job->rc = job->left.parse(self->host_threads, self->tool, merged)) >= 0)
+                job->rc = vgan_euka_flatten(self->graph, &merged, 0, merged.n_reads(), self->host_threads, &hb, &st);
             std::vector<int32_t> c;
             std::vector<uint8_t> p;
             vgan_euka_batch b{};
@@ -855,13 +742,13 @@ struct vgan_euka_gamrun : GamConsumer {
             } else {
                 std::lock_guard<std::mutex> lk(self->mu);
                 for (size_t i = 0; i < b.n_reads; ++i) {
-                    self->idx.push_back((*whr)[b.read_src[i]]);
+                    self->idx.push_back(where[b.read_src[i]]);
                     self->len.push_back(b.read_seq_len[i]);
                     self->clade.push_back(c[i]);
                     self->pass.push_back(p[i]);
                 }
                 self->n_bad += st.n_bad;
-                self->n_host_reads += whr->size();
+                self->n_host_reads += where.size();
             }
             vgan_euka_host_batch_free(hb);
         });
@@ -872,70 +759,30 @@ struct vgan_euka_gamrun : GamConsumer {
 };
 
 extern "C" int vgan_euka_gam_start(const int *devices, int n_lanes, const void *bytes, uint64_t n, const vgan_gampipe_opts *opts, vgan_euka_gamrun **out) {
-    if (!devices || n_lanes <= 0 || (!bytes && n) || !out) return fail(VGAN_EINVAL, "vgan_euka_gam_start: null argument");
-    auto *r = new vgan_euka_gamrun();
-    r->devices.assign(devices, devices + n_lanes);
-    r->bytes = bytes;
-    r->n = n;
-    r->opts = with_defaults(opts, n, n_lanes);
-    r->opts.keep_unmapped = 0;   // readGAM_Euka.h:72: identity == 0 is no fragment of any clade (the messages are counted all the same)
-    r->opts.mark_duplicates = 0; // (euka removes no duplicates)
-    r->df.assign((size_t)n_lanes, nullptr);
-    r->o_clade.resize((size_t)n_lanes), r->o_d.resize((size_t)n_lanes), r->o_pass.resize((size_t)n_lanes);
-    r->lane_mu.resize((size_t)n_lanes);
-    const int cpus = r->opts.n_threads > 0 ? r->opts.n_threads : (int)usable_cpus();
-    r->host_threads = std::max(1, std::min(8, cpus / std::max(1, n_lanes * r->opts.slots)));
-    r->coord = std::thread([r] {
-        r->rc = gampipe_run(r->bytes, r->n, r->devices, r->opts, *r, &r->pst);
-        if (r->rc < 0) r->err = last_error();
+    return gamrun_start("euka", devices, n_lanes, bytes, n, opts, out, [](vgan_euka_gamrun &r) {
+        r.opts.keep_unmapped = 0;   // readGAM_Euka.h:72: identity == 0 is no fragment of any clade (the messages are counted all the same)
+        r.opts.mark_duplicates = 0; // (euka removes no duplicates)
+        r.o_clade.resize(r.devices.size()), r.o_d.resize(r.devices.size()), r.o_pass.resize(r.devices.size());
     });
-    *out = r;
-    return VGAN_OK;
 }
 
 extern "C" int vgan_euka_gam_attach(vgan_euka_gamrun *r, vgan_euka_ctx *const *ctxs, int n_ctx, const vgan_graph *graph) {
-    if (!r || !ctxs || !graph) return fail(VGAN_EINVAL, "vgan_euka_gam_attach: null argument");
-    if (n_ctx != (int)r->devices.size()) return fail(VGAN_EINVAL, "vgan_euka_gam_attach: %d contexts for %zu lanes", n_ctx, r->devices.size());
-    {
-        std::lock_guard<std::mutex> lk(r->mu);
-        if (r->attached) return fail(VGAN_ESTATE, "vgan_euka_gam_attach: called twice");
-        r->ctx.assign(ctxs, ctxs + n_ctx);
-        r->graph = graph;
-        r->attached = true;
-    }
-    r->cv.notify_all();
-    return VGAN_OK;
+    return gamrun_attach("euka", r, ctxs, n_ctx, graph);
 }
 
 extern "C" int vgan_euka_gam_finish(vgan_euka_gamrun *r, vgan_euka_gam_result *res, vgan_gampipe_stats *pstats) {
     if (!r) return fail(VGAN_EINVAL, "vgan_euka_gam_finish: null argument");
     if (res) memset(res, 0, sizeof *res);
-    {
-        std::lock_guard<std::mutex> lk(r->mu);
-        if (!r->attached) r->gave_up = true;
-    }
-    r->cv.notify_all();
-    if (r->coord.joinable()) r->coord.join();
-    for (auto &j : r->bg) {
-        if (j->t.joinable()) j->t.join();
-        if (j->rc < 0 && r->rc >= 0) {
-            r->rc = j->rc;
-            r->err = "the reads left to the host: " + j->err;
-        }
-    }
+    r->join();
     r->bg.clear();
     for (size_t l = 0; l < r->df.size(); ++l) {
         if (l < r->ctx.size() && r->ctx[l]) (void)vgan_euka_synchronize(r->ctx[l]);
-        r->df_bytes += euka_devflat_device_bytes(r->df[l]) + r->o_clade[l].cap + r->o_d[l].cap + r->o_pass[l].cap;
+        r->pst.device_bytes += euka_devflat_device_bytes(r->df[l]) + r->o_clade[l].cap + r->o_d[l].cap + r->o_pass[l].cap;
         vgan_euka_devflat_free(r->df[l]);
         r->df[l] = nullptr;
         if (l < r->devices.size()) (void)hipSetDevice(r->devices[l]);
         r->o_clade[l].release(), r->o_d[l].release(), r->o_pass[l].release();
     }
-    r->pst.device_bytes += r->df_bytes;
-    r->pst.n_host_reads = r->n_host_reads;
-    r->pst.n_device_reads = r->n_device_reads;
-    r->pst.ms_wait_contexts = r->ms_wait_contexts;
     if (pstats) *pstats = r->pst;
     if (r->rc < 0) return fail(r->rc, "%s", r->err.c_str());
     { // the per-read lists in the order of the file: every index below n_mapped occurs at most once -- a placement, not a sort

@@ -11,6 +11,7 @@
 #include <stdexcept>
 #include <fcntl.h>
 #include <signal.h>
+#include <sys/mman.h>
 #include <sys/prctl.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -126,20 +127,6 @@ struct EarlyLeave {
     }
 };
 
-inline int parse_int(const std::string &v, const char *flag, const char *tool);
-// "0,1,3" -> GPU indices appended to out (--gpus / VGAN_GPUS)
-inline void parse_gpu_list(const std::string &v, const char *flag, const char *tool, std::vector<int> &out) {
-    size_t p0 = 0;
-    while (p0 <= v.size()) {
-        size_t c1 = v.find(',', p0);
-        if (c1 == std::string::npos) c1 = v.size();
-        const int d = parse_int(v.substr(p0, c1 - p0), flag, tool);
-        if (d < 0) die(std::string(tool) + " Error, " + flag + " needs non-negative GPU indices");
-        out.push_back(d);
-        p0 = c1 + 1;
-    }
-}
-
 inline void check(int rc, const char *what) {
     if (rc < 0) die(std::string("[vgan] ") + what + ": " + vgan_last_error());
 }
@@ -185,13 +172,78 @@ inline void reject_fasta(const std::string &f, const char *tool) {
         if (ends_with(f, suf)) die(std::string(tool) + " Input file must be FASTQ, not FASTA");
 }
 
+// Which GPUs: the value of --gpus, else the environment's VGAN_GPUS, else the one of `device`.  A list ("0,1,3"; an index may repeat: several
+// contexts on one GPU) or `all`, every visible GPU -- which waits for the runtime the warm-up brings up (at once when it has not started).
+// Empty for `all` when no GPU is visible: the caller says so in its own words.
+inline std::vector<int> resolve_gpus(const std::string &flag_value, int device, const char *tool, DeviceWarm &warm) {
+    std::string v = flag_value;
+    const char *src = "--gpus";
+    if (v.empty())
+        if (const char *e = getenv("VGAN_GPUS")) v = e, src = "VGAN_GPUS";
+    std::vector<int> out;
+    if (v.empty()) out.push_back(device);
+    else if (v == "all") {
+        warm.wait_runtime();
+        for (int d = 0, n = vgan_device_count(); d < n; ++d) out.push_back(d);
+    } else
+        for (size_t p0 = 0; p0 <= v.size();) {
+            size_t c1 = v.find(',', p0);
+            if (c1 == std::string::npos) c1 = v.size();
+            const int d = parse_int(v.substr(p0, c1 - p0), src, tool);
+            if (d < 0) die(std::string(tool) + " Error, " + src + " needs non-negative GPU indices");
+            out.push_back(d);
+            p0 = c1 + 1;
+        }
+    return out;
+}
+
+// A GAM file mapped into memory when it is BGZF (the device front end's input), else nothing.  <env_name>=0 / 1: never / whatever its
+// size; otherwise files of min_bytes and more.
+struct GamMap {
+    const uint8_t *p = nullptr;
+    size_t n = 0;
+    GamMap() = default;
+    GamMap(GamMap &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; }
+    GamMap &operator=(GamMap &&o) noexcept {
+        std::swap(p, o.p), std::swap(n, o.n);
+        return *this;
+    }
+    ~GamMap() {
+        if (p) munmap(const_cast<uint8_t *>(p), n);
+    }
+    explicit operator bool() const { return p != nullptr; }
+};
+inline GamMap map_bgzf_gam(const std::string &path, const char *env_name, uint64_t min_bytes) {
+    GamMap g;
+    const char *e = getenv(env_name);
+    struct stat sb;
+    if ((e && e[0] == '0') || stat(path.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode) || !((e && e[0] == '1') || (uint64_t)sb.st_size >= min_bytes) || sb.st_size <= 28)
+        return g;
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) return g;
+    void *m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+    close(fd);
+    if (m == MAP_FAILED) return g;
+    const uint8_t *b = (const uint8_t *)m;
+    if (!(b[0] == 0x1f && b[1] == 0x8b && b[2] == 8 && (b[3] & 4))) { // (BGZF members carry an extra field)
+        munmap(m, (size_t)sb.st_size);
+        return g;
+    }
+    (void)madvise(m, (size_t)sb.st_size, MADV_WILLNEED);
+    g.p = b;
+    g.n = (size_t)sb.st_size;
+    return g;
+}
+
 // frees a C-ABI object on every exit path
 template <class T> struct Handle {
     T *p = nullptr;
     void (*release)(T *);
     explicit Handle(void (*r)(T *)) : release(r) {}
-    ~Handle() {
+    ~Handle() { reset(); }
+    void reset() {
         if (p) release(p);
+        p = nullptr;
     }
     Handle(const Handle &) = delete;
     Handle &operator=(const Handle &) = delete;

@@ -70,7 +70,7 @@ int euka_main(int argc, char **argv) {
     std::string deam5, deam3, out_group, out_dir;
     bool interleaved = false, run_mcmc = true, out_frag = false;
     int n_threads = 1, iter = 10000, burnin = 100, ltp = 5, device = 0; // Euka.cpp:171-190
-    std::vector<int> gpu_list;
+    std::string gpu_spec;
     int min_bins = 6, min_reads = 10, min_mq = 29, max_bins = 0;
     double entropy = 1.17;
     uint64_t seed = 0;
@@ -140,18 +140,8 @@ int euka_main(int argc, char **argv) {
         else if (a == "--device") {
             device = parse_int(need("--device"), "--device", T);
             if (device < 0) die("[euka] Error, --device needs a non-negative GPU index");
-        } else if (a == "--gpus") { // GPU indices, comma separated: one device context (and host thread) each
-            const std::string v = need("--gpus");
-            size_t p0 = 0;
-            while (p0 <= v.size()) {
-                size_t c1 = v.find(',', p0);
-                if (c1 == std::string::npos) c1 = v.size();
-                const int d = parse_int(v.substr(p0, c1 - p0), "--gpus", T);
-                if (d < 0) die("[euka] Error, --gpus needs non-negative GPU indices");
-                gpu_list.push_back(d);
-                p0 = c1 + 1;
-            }
-        } else die("[euka] Error, unrecognized option " + a);
+        } else if (a == "--gpus") gpu_spec = need("--gpus"); // GPU indices, comma separated: one device context (and host thread) each
+        else die("[euka] Error, unrecognized option " + a);
     }
     (void)interleaved;
     if (!fq1.empty() || !fq2.empty())
@@ -165,69 +155,32 @@ int euka_main(int argc, char **argv) {
     if (run_mcmc && iter - burnin - 1 <= 0) die("[euka] Error, --iter must exceed --burnin + 1");
 
     PhaseTimer pt("euka");
-    // which GPUs: --gpus LIST, the environment's VGAN_GPUS (`all` or a list), or the one of --device
-    if (gpu_list.empty()) {
-        const char *e = getenv("VGAN_GPUS");
-        if (e && std::string(e) == "all") {
-            const int n_visible = vgan_device_count();
-            for (int d = 0; d < n_visible; ++d) gpu_list.push_back(d);
-        } else if (e && *e) {
-            const std::string v = e;
-            size_t p0 = 0;
-            while (p0 <= v.size()) {
-                size_t c1 = v.find(',', p0);
-                if (c1 == std::string::npos) c1 = v.size();
-                const int d = parse_int(v.substr(p0, c1 - p0), "VGAN_GPUS", T);
-                if (d < 0) die("[euka] Error, VGAN_GPUS needs non-negative GPU indices");
-                gpu_list.push_back(d);
-                p0 = c1 + 1;
-            }
-        }
-        if (gpu_list.empty()) gpu_list.push_back(device);
-    }
+    DeviceWarm warm; // (the runtime and the run's code objects, beside the tables' loading)
+    const std::vector<int> gpu_list = resolve_gpus(gpu_spec, device, T, warm); // (before the warm-up: `all` counts the GPUs at once)
     // A long BGZF input: the front end runs ON THE DEVICE (vgan_euka_gam_*: the file in pieces through inflate, framing, protobuf walk
     // and euka's flatten as kernels, piece i to context i mod n; csrc/gam_pipe.hip, euka_flatten_kernels.hip); the host parses only the
     // reads the device flatten leaves (indels, soft clips).  VGAN_EUKA_DEVICE_GAM=0 / 1: never / whenever the input is a regular file.
     // --outFrag needs the reads' names, which the device does not keep: the host pipeline's.  Anything the device refuses goes through
     // the host pipeline as well.
-    struct FileMap {
-        const uint8_t *p = nullptr;
-        size_t n = 0;
-        ~FileMap() {
-            if (p) munmap(const_cast<uint8_t *>(p), n);
-        }
-    } gam_map;
-    struct GdRun {
-        vgan_euka_gamrun *r = nullptr;
-        ~GdRun() { vgan_euka_gam_free(r); }
-    };
-    bool device_gam = false;
-    {
-        const char *e = getenv("VGAN_EUKA_DEVICE_GAM");
-        struct stat sb;
-        if (!(e && e[0] == '0') && !out_frag && stat(gam.c_str(), &sb) == 0 && S_ISREG(sb.st_mode) && ((e && e[0] == '1') || (uint64_t)sb.st_size >= (128ull << 20)) &&
-            sb.st_size > 28) {
-            const int fd = open(gam.c_str(), O_RDONLY);
-            if (fd >= 0) {
-                void *m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-                close(fd);
-                if (m != MAP_FAILED) {
-                    gam_map.p = (const uint8_t *)m;
-                    gam_map.n = (size_t)sb.st_size;
-                    device_gam = gam_map.p[0] == 0x1f && gam_map.p[1] == 0x8b && gam_map.p[2] == 8 && (gam_map.p[3] & 4); // (BGZF members carry an extra field)
-                    if (device_gam) (void)madvise(m, gam_map.n, MADV_WILLNEED);
-                }
-            }
-        }
-    }
-    DeviceWarm warm; // (the runtime and the run's code objects, beside the tables' loading)
+    GamMap gam_map;
+    if (!out_frag) gam_map = map_bgzf_gam(gam, "VGAN_EUKA_DEVICE_GAM", 128ull << 20);
+    bool device_gam = (bool)gam_map;
     warm.start(gpu_list.empty() ? 0 : gpu_list[0], VGAN_PRELOAD_EUKA | (device_gam ? VGAN_PRELOAD_GAM : 0u));
     GamReader reader; // unmapped reads are kept so that they are counted
-    GdRun gd; // (started now: upload, inflate, framing and parse need neither tables nor contexts and run beside their set-up)
+    Handle<vgan_graph> graph(vgan_graph_free);
+    struct Contexts {
+        std::vector<vgan_euka_ctx *> v;
+        ~Contexts() {
+            for (auto c : v) vgan_euka_destroy(c);
+        }
+    } ctxs;
+    // (started now: upload, inflate, framing and parse need neither tables nor contexts and run beside their set-up; declared after the
+    // graph and the contexts, on an error's unwinding it is freed -- its threads joined -- before they go)
+    Handle<vgan_euka_gamrun> gd(vgan_euka_gam_free);
     if (device_gam) {
         vgan_gampipe_opts po{};
         po.n_threads = n_threads;
-        if (vgan_euka_gam_start(gpu_list.data(), (int)gpu_list.size(), gam_map.p, gam_map.n, &po, &gd.r) < 0) device_gam = false;
+        if (vgan_euka_gam_start(gpu_list.data(), (int)gpu_list.size(), gam_map.p, gam_map.n, &po, &gd.p) < 0) device_gam = false;
     }
     if (!device_gam) reader.start(gam, 1);
     Handle<vgan_damage> dmg(vgan_damage_free);
@@ -250,7 +203,6 @@ int euka_main(int argc, char **argv) {
         if (!found) die("[euka] Outgroup not found in reference graph");
     }
     std::cerr << "Reading in variation graph ..." << std::endl;
-    Handle<vgan_graph> graph(vgan_graph_free);
     check(vgan_graph_load((prefix + graph_ext).c_str(), nullptr, &graph.p), "loading graph");
     if (graph_ext == ".og") { // Euka.cpp:372,419: the haplotype index beside the graph
         vgan_graph_view ggv;
@@ -265,19 +217,6 @@ int euka_main(int argc, char **argv) {
     vgan_euka_params prm;
     prm.min_mapq = (uint32_t)min_mq;
     prm.length_to_prof = ltp;
-    struct Contexts {
-        std::vector<vgan_euka_ctx *> v;
-        ~Contexts() {
-            for (auto c : v) vgan_euka_destroy(c);
-        }
-    } ctxs;
-    struct GdStop { // (an error's unwinding: the front end's threads use the contexts -- they are joined before the contexts go)
-        vgan_euka_gamrun *&r;
-        ~GdStop() {
-            vgan_euka_gam_free(r);
-            r = nullptr;
-        }
-    } gd_stop{gd.r};
     for (int d : gpu_list) {
         vgan_euka_ctx *c = nullptr;
         check(vgan_euka_create(&dv, &dmv, &prm, d, &c), "creating the device context");
@@ -297,10 +236,11 @@ int euka_main(int argc, char **argv) {
     if (device_gam) {
         vgan_euka_gam_result gr{};
         vgan_gampipe_stats ps{};
-        int rc = vgan_euka_gam_attach(gd.r, ctxs.v.data(), (int)K, graph.p);
-        if (rc >= 0) rc = vgan_euka_gam_finish(gd.r, &gr, &ps);
+        int rc = vgan_euka_gam_attach(gd.p, ctxs.v.data(), (int)K, graph.p);
+        if (rc >= 0) rc = vgan_euka_gam_finish(gd.p, &gr, &ps);
         if (rc < 0) { // nothing else has been accumulated: the contexts are cleared and the host pipeline takes the file from its start
             std::cerr << "[euka] the device front end does not take this input (" << vgan_last_error() << "): the host pipeline does" << std::endl;
+            gd.reset(); // (the run's pieces let go of their device buffers first)
             for (auto c : ctxs.v) check(vgan_euka_reset(c), "reset");
             device_gam = false;
             reader.start(gam, 1);

@@ -161,32 +161,9 @@ int haplocart(int argc, char **argv) {
     // i mod n: every device inflates and parses its own pieces.  The host pipeline costs ~3 us of CPU per read, which on a CPU quota
     // is what a long input's wall time follows.  VGAN_HC_DEVICE_GAM=0 / 1: never / whenever the input is a regular file;
     // anything the device refuses (not BGZF, a stream its segment walks cannot frame, no memory) goes through the host pipeline.
-    struct FileMap {
-        const uint8_t *p = nullptr;
-        size_t n = 0;
-        ~FileMap() {
-            if (p) munmap(const_cast<uint8_t *>(p), n);
-        }
-    } gam_map;
-    bool device_gam = false;
-    {
-        const char *e = getenv("VGAN_HC_DEVICE_GAM");
-        struct stat sb;
-        if (!(e && e[0] == '0') && !per_read && fastafilename.empty() && stat(gamfilename.c_str(), &sb) == 0 && S_ISREG(sb.st_mode) &&
-            ((e && e[0] == '1') || (uint64_t)sb.st_size >= (384ull << 20)) && sb.st_size > 28) {
-            const int fd = open(gamfilename.c_str(), O_RDONLY);
-            if (fd >= 0) {
-                void *m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-                close(fd);
-                if (m != MAP_FAILED) {
-                    gam_map.p = (const uint8_t *)m;
-                    gam_map.n = (size_t)sb.st_size;
-                    device_gam = gam_map.p[0] == 0x1f && gam_map.p[1] == 0x8b && gam_map.p[2] == 8 && (gam_map.p[3] & 4); // (BGZF members carry an extra field)
-                    if (device_gam) (void)madvise(m, gam_map.n, MADV_WILLNEED);
-                }
-            }
-        }
-    }
+    GamMap gam_map;
+    if (!per_read && fastafilename.empty()) gam_map = map_bgzf_gam(gamfilename, "VGAN_HC_DEVICE_GAM", 384ull << 20);
+    bool device_gam = (bool)gam_map;
     if (!device_gam) check(vgan_gam_stream_open(gamfilename.c_str(), 0, &stream.s), "reading GAM");
     // the HIP runtime comes up on a thread of its own while the graph is read, the run's code objects behind it (cli_util.h: DeviceWarm)
     DeviceWarm warm;
@@ -200,38 +177,23 @@ int haplocart(int argc, char **argv) {
     // which GPUs: --gpus LIST, the environment's VGAN_GPUS, or the one of --device
     // (the HIP runtime is still coming up: only "--gpus all" has to wait for it here, to know how many contexts there will
     // be; otherwise the first chunks are decoded and flattened beside it and the context thread below is the one that waits)
-    if (gpu_spec.empty())
-        if (const char *e = getenv("VGAN_GPUS")) gpu_spec = e;
-    if (gpu_spec == "all") {
-        warm.wait_runtime();
-        const int n_visible = vgan_device_count();
-        if (n_visible <= 0) die("[HaploCart] no HIP device is visible: the likelihood path runs on the GPU only");
-        for (int d = 0; d < n_visible; ++d) gpu_list.push_back(d);
-    } else if (!gpu_spec.empty()) {
-        size_t p0 = 0;
-        while (p0 <= gpu_spec.size()) {
-            size_t c1 = gpu_spec.find(',', p0);
-            if (c1 == std::string::npos) c1 = gpu_spec.size();
-            const int d = parse_int(gpu_spec.substr(p0, c1 - p0), "--gpus", "[HaploCart]");
-            if (d < 0) die("[HaploCart] Error, --gpus needs non-negative GPU indices");
-            gpu_list.push_back(d);
-            p0 = c1 + 1;
+    gpu_list = resolve_gpus(gpu_spec, device, "[HaploCart]", warm);
+    if (gpu_list.empty()) die("[HaploCart] no HIP device is visible: the likelihood path runs on the GPU only");
+    struct Contexts { // one device context per entry of the list (an index may repeat: several contexts on one GPU)
+        std::vector<vgan_hc_ctx *> v;
+        ~Contexts() {
+            for (auto c : v) vgan_hc_destroy(c);
         }
-    }
-    if (gpu_list.empty()) gpu_list.push_back(device);
+    } ctxs;
     // (the device front end needs neither graph nor contexts for its first stages: it starts now -- the member index of the first piece,
-    // then, as soon as the HIP runtime is up, upload, inflate, framing and parse -- beside the graph load and the contexts' set-up)
-    struct GdRun {
-        vgan_hc_gamrun *r = nullptr;
-        ~GdRun() {
-            if (r) (void)vgan_hc_gam_finish(r, nullptr, nullptr); // (an error's unwinding: the pieces give up, the threads are joined)
-        }
-    } gd;
+    // then, as soon as the HIP runtime is up, upload, inflate, framing and parse -- beside the graph load and the contexts' set-up; declared
+    // after the contexts, on an error's unwinding it is finished -- its threads joined -- before they go)
+    Handle<vgan_hc_gamrun> gd([](vgan_hc_gamrun *r) { (void)vgan_hc_gam_finish(r, nullptr, nullptr); });
     if (device_gam) {
         vgan_gampipe_opts po{};
         po.mark_duplicates = rmdup ? 1 : 0;
         po.n_threads = n_threads;
-        if (vgan_hc_gam_start(gpu_list.data(), (int)gpu_list.size(), gam_map.p, gam_map.n, &po, &gd.r) < 0) {
+        if (vgan_hc_gam_start(gpu_list.data(), (int)gpu_list.size(), gam_map.p, gam_map.n, &po, &gd.p) < 0) {
             device_gam = false;
             check(vgan_gam_stream_open(gamfilename.c_str(), 0, &stream.s), "reading GAM");
         }
@@ -279,19 +241,6 @@ int haplocart(int argc, char **argv) {
     prm.background_error_prob = background_error_prob;
     prm.use_background_error_prob = !fastafilename.empty(); // HaploCart.cpp:397-400
     prm.is_consensus_fasta = !fastafilename.empty();
-    struct Contexts { // one device context per entry of the list (an index may repeat: several contexts on one GPU)
-        std::vector<vgan_hc_ctx *> v;
-        ~Contexts() {
-            for (auto c : v) vgan_hc_destroy(c);
-        }
-    } ctxs;
-    struct GdStop { // (an error's unwinding: the front end's threads use the contexts -- they are joined before the contexts go)
-        vgan_hc_gamrun *&r;
-        ~GdStop() {
-            if (r) (void)vgan_hc_gam_finish(r, nullptr, nullptr);
-            r = nullptr;
-        }
-    } gd_stop{gd.r};
     // the contexts come up on a thread of their own (mask transposition, uploads: ~0.2 s) while this one already flattens
     // the first chunk of reads, which needs the graph only
     std::atomic<bool> contexts_up{false}; // (the lanes flatten on the host until the device can: see the chunk loop)
@@ -498,9 +447,9 @@ int haplocart(int argc, char **argv) {
         const auto t0 = std::chrono::steady_clock::now();
         vgan_hc_flatten_stats st{};
         vgan_gampipe_stats ps{};
-        int rc = vgan_hc_gam_attach(gd.r, ctxs.v.data(), (int)ctxs.v.size(), graph);
-        vgan_hc_gamrun *run = gd.r;
-        gd.r = nullptr;
+        int rc = vgan_hc_gam_attach(gd.p, ctxs.v.data(), (int)ctxs.v.size(), graph);
+        vgan_hc_gamrun *run = gd.p;
+        gd.p = nullptr;
         const int rc2 = vgan_hc_gam_finish(run, &st, &ps);
         if (rc >= 0) rc = rc2;
         if (rc < 0) {

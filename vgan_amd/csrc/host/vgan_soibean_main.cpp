@@ -74,7 +74,7 @@ int soibean_main(int argc, char **argv) {
     std::string sbdir = "../share/vgan/soibean_dir/", treedir, dbprefix = "soibean_db", gam, fq1, fq2, out_prefix = "beanOut", deam5, deam3;
     bool run_mcmc = true, dbprefix_found = false, rand_start = false, specified_k = false, specified_deam = false;
     int n_threads = 1, iter = 500000, burnin = 75000, chains = 4, k = 1, penalty = 7, device = 0; // soibean.cpp:209-240
-    std::vector<int> gpu_list;
+    std::string gpu_spec;
     uint64_t seed = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -136,9 +136,8 @@ int soibean_main(int argc, char **argv) {
         else if (a == "--device") {
             device = parse_int(need("--device"), "--device", T);
             if (device < 0) die("[soibean] Error, --device needs a non-negative GPU index");
-        } else if (a == "--gpus") {
-            parse_gpu_list(need("--gpus"), "--gpus", T, gpu_list);
-        } else die("[soibean] Error, unrecognized option " + a);
+        } else if (a == "--gpus") gpu_spec = need("--gpus");
+        else die("[soibean] Error, unrecognized option " + a);
     }
     if (!fq1.empty() || !fq2.empty())
         die("[soibean] FASTQ input needs vg giraffe in-process, which this build does not have; map with vg and pass -g");
@@ -155,64 +154,43 @@ int soibean_main(int argc, char **argv) {
     if (!is_readable_input(gam)) die("[soibean] Error, GAM input file " + gam + " does not exist");
 
     PhaseTimer pt("soibean");
-    if (gpu_list.empty()) {
-        if (const char *e = getenv("VGAN_GPUS")) {
-            if (std::string(e) == "all")
-                for (int d = 0; d < vgan_device_count(); ++d) gpu_list.push_back(d);
-            else if (*e) parse_gpu_list(e, "VGAN_GPUS", T, gpu_list);
-        }
-        if (gpu_list.empty()) gpu_list.push_back(device);
-    }
+    DeviceWarm warm; // (the runtime and the run's code objects, beside the graph's and the tree's loading)
+    const std::vector<int> gpu_list = resolve_gpus(gpu_spec, device, T, warm); // (before the warm-up: `all` counts the GPUs at once)
     // A long BGZF input: the front end runs ON THE DEVICE (vgan_sb_gam_*: the file in pieces through inflate, framing, protobuf walk and
     // soibean's flatten as kernels, piece i to context i mod n; csrc/gam_pipe.hip, sb_flatten_kernels.hip, sb_gam_run.hip); the host parses
     // only the reads the device flatten leaves (indels, soft clips).  VGAN_SB_DEVICE_GAM=0 / 1: never / whenever the input is a regular
     // file.  Anything the device refuses goes through the host pipeline.
-    struct FileMap {
-        const uint8_t *p = nullptr;
-        size_t n = 0;
-        ~FileMap() {
-            if (p) munmap(const_cast<uint8_t *>(p), n);
-        }
-    } gam_map;
-    struct GdRun {
-        vgan_sb_gamrun *r = nullptr;
-        ~GdRun() { vgan_sb_gam_free(r); }
-    };
-    bool device_gam = false;
-    {
-        const char *e = getenv("VGAN_SB_DEVICE_GAM");
-        struct stat sb;
-        if (!(e && e[0] == '0') && vgan_device_count() > 0 && stat(gam.c_str(), &sb) == 0 && S_ISREG(sb.st_mode) &&
-            ((e && e[0] == '1') || (uint64_t)sb.st_size >= (128ull << 20)) && sb.st_size > 28) {
-            const int fd = open(gam.c_str(), O_RDONLY);
-            if (fd >= 0) {
-                void *m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-                close(fd);
-                if (m != MAP_FAILED) {
-                    gam_map.p = (const uint8_t *)m;
-                    gam_map.n = (size_t)sb.st_size;
-                    device_gam = gam_map.p[0] == 0x1f && gam_map.p[1] == 0x8b && gam_map.p[2] == 8 && (gam_map.p[3] & 4); // (BGZF members carry an extra field)
-                    if (device_gam) (void)madvise(m, gam_map.n, MADV_WILLNEED);
-                }
-            }
-        }
-        for (int d : gpu_list)
-            if (d >= vgan_device_count()) device_gam = false; // (reported below, once the tables are read)
-    }
-    DeviceWarm warm; // (the runtime and the run's code objects, beside the graph's and the tree's loading)
+    GamMap gam_map;
+    if (vgan_device_count() > 0) gam_map = map_bgzf_gam(gam, "VGAN_SB_DEVICE_GAM", 128ull << 20);
+    bool device_gam = (bool)gam_map;
+    for (int d : gpu_list)
+        if (d >= vgan_device_count()) device_gam = false; // (reported below, once the tables are read)
     warm.start(gpu_list.empty() ? 0 : gpu_list[0], VGAN_PRELOAD_SB | (device_gam ? VGAN_PRELOAD_GAM : 0u));
     GamReader reader;
-    GdRun gd; // (started now: upload, inflate, framing and parse need neither graph nor contexts and run beside their set-up)
+    Handle<vgan_graph> graph(vgan_graph_free);
+    // one device context per GPU (--gpus / VGAN_GPUS; a GPU may be named twice: two contexts on it), the reads dealt to them
+    // once in contiguous shares: MCMC.cpp:739 runs its loop over the reads in parallel with `reduction(+:logLike)`, here the
+    // reduction runs over devices -- in integers (vgan_sb_sum), so the number of devices does not change a bit of the result
+    struct Contexts {
+        std::vector<vgan_sb_ctx *> v;
+        vgan_sb_group *group = nullptr;
+        ~Contexts() {
+            vgan_sb_group_free(group);
+            for (auto c : v) vgan_sb_destroy(c);
+        }
+    } ctxs;
+    // (started now: upload, inflate, framing and parse need neither graph nor contexts and run beside their set-up; declared after the
+    // graph and the contexts, on an error's unwinding it is freed -- its threads joined -- before they go)
+    Handle<vgan_sb_gamrun> gd(vgan_sb_gam_free);
     if (device_gam) {
         vgan_gampipe_opts po{};
         po.n_threads = n_threads;
-        if (vgan_sb_gam_start(gpu_list.data(), (int)gpu_list.size(), gam_map.p, gam_map.n, &po, &gd.r) < 0) device_gam = false;
+        if (vgan_sb_gam_start(gpu_list.data(), (int)gpu_list.size(), gam_map.p, gam_map.n, &po, &gd.p) < 0) device_gam = false;
     }
     if (!device_gam) reader.start(gam, 0);
     Handle<vgan_damage> dmg(vgan_damage_free);
     check(vgan_damage_load(deam5.empty() ? nullptr : deam5.c_str(), deam3.empty() ? nullptr : deam3.c_str(), &dmg.p), "damage profiles");
     std::cerr << "Reading in variation graph ..." << std::endl;
-    Handle<vgan_graph> graph(vgan_graph_free);
     check(vgan_graph_load(gfa.c_str(), nullptr, &graph.p), "loading graph");
     vgan_graph_view gv;
     check(vgan_graph_view_get(graph.p, &gv), "graph view");
@@ -273,24 +251,6 @@ int soibean_main(int argc, char **argv) {
     vgan_damage_view dmv;
     check(vgan_damage_view_get(dmg.p, &dmv), "damage view");
     vgan_sb_params prm{penalty, 0};
-    // one device context per GPU (--gpus / VGAN_GPUS; a GPU may be named twice: two contexts on it), the reads dealt to them
-    // once in contiguous shares: MCMC.cpp:739 runs its loop over the reads in parallel with `reduction(+:logLike)`, here the
-    // reduction runs over devices -- in integers (vgan_sb_sum), so the number of devices does not change a bit of the result
-    struct Contexts {
-        std::vector<vgan_sb_ctx *> v;
-        vgan_sb_group *group = nullptr;
-        ~Contexts() {
-            vgan_sb_group_free(group);
-            for (auto c : v) vgan_sb_destroy(c);
-        }
-    } ctxs;
-    struct GdStop { // (an error's unwinding: the front end's threads use the contexts -- they are joined before the contexts go)
-        vgan_sb_gamrun *&r;
-        ~GdStop() {
-            vgan_sb_gam_free(r);
-            r = nullptr;
-        }
-    } gd_stop{gd.r};
     for (int d : gpu_list) {
         if (d >= vgan_device_count()) die("[soibean] Error, GPU " + std::to_string(d) + " asked for, " + std::to_string(vgan_device_count()) + " visible");
         vgan_sb_ctx *c = nullptr;
@@ -304,10 +264,11 @@ int soibean_main(int argc, char **argv) {
     if (device_gam) {
         vgan_sb_gam_result gr{};
         vgan_gampipe_stats ps{};
-        int rc = vgan_sb_gam_attach(gd.r, ctxs.v.data(), (int)n_ctx, graph.p);
-        if (rc >= 0) rc = vgan_sb_gam_finish(gd.r, &gr, &ps);
+        int rc = vgan_sb_gam_attach(gd.p, ctxs.v.data(), (int)n_ctx, graph.p);
+        if (rc >= 0) rc = vgan_sb_gam_finish(gd.p, &gr, &ps);
         if (rc < 0) { // (vgan_sb_precompute replaces a context's tables: the host pipeline takes the file from its start)
             std::cerr << "[soibean] the device front end does not take this input (" << vgan_last_error() << "): the host pipeline does" << std::endl;
+            gd.reset(); // (the run's pieces let go of their device buffers first)
             device_gam = false;
             reader.start(gam, 0);
         } else {
@@ -320,8 +281,7 @@ int soibean_main(int argc, char **argv) {
                         ps.compressed_bytes / 1e6, ps.inflated_bytes / 1e6, (unsigned long long)ps.n_pieces, (long long)n_ctx, (unsigned long long)ps.n_messages, (unsigned long long)ps.n_reads,
                         (unsigned long long)ps.n_host_reads, ps.ms_wall, gr.ms_tables, ps.ms_upload, ps.ms_inflate, ps.ms_frame, ps.ms_parse, ps.ms_consume, ps.device_bytes / 1e9);
         }
-        vgan_sb_gam_free(gd.r); // (the batch's memory back: the tables stay in the contexts)
-        gd.r = nullptr;
+        gd.reset(); // (the batch's memory back: the tables stay in the contexts)
     }
     Handle<vgan_alnset> aln(vgan_aln_free);
     vgan_alnset_view av{};
